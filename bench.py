@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- encode+decode GB/s (input bytes) of the HIP hot path, with roofline and CPU baseline.
 
-  python bench.py [--gpus N --steps K --warmup W --workload NAME]
+  python bench.py [--gpus N --steps K --warmup W --workload NAME --dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 
@@ -47,6 +47,13 @@ WORKLOADS = {
 SECONDARY_1GPU = [("text8g", 5, 3), ("lowentropy", 5, 3), ("random256m", 20, 5), ("text", 10, 3), ("text_32m", 10, 3)]
 SECONDARY_NGPU = [("text", 10, 3), ("lowentropy", 5, 3)]  # configs 4 and 5 exactly, at N = 8
 
+# --dump-outputs: what a caller of the timed step receives, at most this many elements per array (a fixed, seeded,
+# stratified sample of longer arrays).  Total <= 56 MiB + .npy headers, under the 64 MB cap.
+DUMP_SEED = 0xD0C2
+DUMP_CAPS = {"payload": 1 << 21, "comp_size": 1 << 20, "comp_off": 1 << 20, "code_lengths": 1 << 21, "status": 1 << 20,
+             "total": 1, "decoded": 1 << 21, "decode_status": 1 << 20, "decode_errpos": 1 << 20}
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+
 
 class Env:
     """Process-wide pieces every workload shares."""
@@ -77,9 +84,48 @@ class Env:
         self.sharding = sharding
 
 
-def run_workload(env, name, steps, warmup, verify, per_gpu_override=0, chunk_override=0):
+def _sample_index(np, n, cap):
+    """Positions of a fixed sample of an n-element array: all of them if n <= cap, else one seeded position in each
+    of cap equal strata (sorted, distinct, the same for the same n on every run)."""
+    if n <= cap:
+        return np.arange(n, dtype=np.int64)
+    stride = n // cap
+    rng = np.random.default_rng(DUMP_SEED)
+    return np.arange(cap, dtype=np.int64) * stride + rng.integers(0, stride, cap, dtype=np.int64)
+
+
+def _dump_outputs(env, dump_dir, blk, t_out, dstatus, derrpos, per_gpu):
+    """Writes what the last step handed its caller as DIR/<name>.npy (float32, or float64 where float32 is not exact).
+    Payload bytes at or past `total` (no part of the stream) are written as -1, so the sampled positions depend on the
+    arguments alone.  Returns {name: [elements written, elements of the output]}."""
+    np, torch = env.np, env.torch
+    total = int(blk.total.item())
+    flat = {"payload": (blk.payload[:per_gpu], np.float32), "comp_size": (blk.comp_size, np.float64),
+            "comp_off": (blk.comp_off, np.float64), "code_lengths": (blk.code_lengths.reshape(-1), np.float32),
+            "status": (blk.status, np.float32), "total": (blk.total, np.float64),
+            "decoded": (t_out[:per_gpu], np.float32), "decode_status": (dstatus, np.float32),
+            "decode_errpos": (derrpos, np.float64)}
+    os.makedirs(dump_dir, exist_ok=True)
+    written, nbytes = {}, 0
+    for nm, (t, dt) in flat.items():
+        n = int(t.numel())
+        idx = _sample_index(np, n, DUMP_CAPS[nm])
+        vals = t[torch.from_numpy(idx).to(t.device)].cpu().numpy().astype(dt)
+        if nm == "payload":
+            vals[idx >= total] = -1
+        path = os.path.join(dump_dir, nm + ".npy")
+        np.save(path, vals)
+        nbytes += os.path.getsize(path)
+        written[nm] = [int(idx.size), n]
+    if nbytes > DUMP_MAX_BYTES:
+        raise SystemExit("bench.py --dump-outputs wrote %d bytes, over the %d-byte cap" % (nbytes, DUMP_MAX_BYTES))
+    return written
+
+
+def run_workload(env, name, steps, warmup, verify, per_gpu_override=0, chunk_override=0, dump_dir=None):
     """Times `steps` steps of one workload on a context of its own (the launch-shape hints are per context, so a
-    workload starts like a fresh process would).  Returns the result dict of rank 0's view, value aggregated over ranks."""
+    workload starts like a fresh process would).  Returns the result dict of rank 0's view, value aggregated over ranks.
+    dump_dir: rank 0 writes the outputs of the last timed step there (_dump_outputs)."""
     torch, dist, pkg, world, rank, dev = env.torch, env.dist, env.pkg, env.world, env.rank, env.dev
     gen, seed, per_gpu, chunk, desc = WORKLOADS[name]
     if per_gpu_override:
@@ -149,6 +195,9 @@ def run_workload(env, name, steps, warmup, verify, per_gpu_override=0, chunk_ove
     elapsed = time.perf_counter() - t0
     svc.ctx.set_profiling(False)
     shapes = svc.ctx.launch_shapes()  # (of the timed steps: read before anything else calls into the library)
+    dumped = None
+    if dump_dir and rank == 0:  # before the graph replay below writes the same buffers again
+        dumped = _dump_outputs(env, dump_dir, blk, t_out, dstatus, derrpos, per_gpu)
 
     if world > 1:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev if env.args.backend == "nccl" else "cpu")
@@ -199,6 +248,8 @@ def run_workload(env, name, steps, warmup, verify, per_gpu_override=0, chunk_ove
         torch.cuda.synchronize(dev)
         if graph is not None:
             res["graph_replay"] = graph
+        if dumped is not None:
+            res["dump_outputs"] = {"dir": dump_dir, "arrays": dumped}
         res["sha256_per_chunk"] = {"gbps": round(2 * per_gpu / (time.perf_counter() - ts) / 1e9, 2), "chunks": k_local,
                                    "note": "one lane per chunk; throughput scales with the number of chunks"}
     svc.close()
@@ -321,11 +372,15 @@ def main():
                          "to rehearse the N>1 code path on a one-GPU box")
     ap.add_argument("--single-device", action="store_true",
                     help="rehearsal only: every rank uses cuda:0 (needs --backend gloo)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step of the headline workload returned (rank 0's payload, sizes, "
+                         "offsets, code lengths, statuses, total, decoded bytes) as DIR/<name>.npy, float32/float64, "
+                         "at most 64 MB (fixed seeded samples of larger arrays)")
     args = ap.parse_args()
     env = Env(args)
 
     head = run_workload(env, args.workload, args.steps, args.warmup, not args.no_verify, args.bytes_per_gpu,
-                        args.chunk_bytes)
+                        args.chunk_bytes, dump_dir=args.dump_outputs)
     secondary = {}
     if not args.no_secondary and not args.bytes_per_gpu and not args.chunk_bytes:
         for name, st, wu in (SECONDARY_1GPU if env.world == 1 else SECONDARY_NGPU):
@@ -340,7 +395,7 @@ def main():
                 "n_gpus": env.world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": head["ms_per_step"],
                 "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8", "data": "synthetic"}
         for k in ("config", "verified_bit_exact_round_trip", "roofline", "roundtrip_roofline", "split", "launch_shapes",
-                  "mixed_launch_shapes", "kernels", "graph_replay", "sha256_per_chunk"):
+                  "mixed_launch_shapes", "kernels", "graph_replay", "sha256_per_chunk", "dump_outputs"):
             if k in head:
                 line[k] = head[k]
         if secondary:

@@ -69,6 +69,7 @@ __global__ __launch_bounds__(256) void gen_text(uint8_t* __restrict__ d, size_t 
         for (int c = '0'; c <= '9'; c++) { order[m++] = (uint8_t)c; used[c] = true; }
         for (int c = 33; c < 127; c++) if (!used[c]) order[m++] = (uint8_t)c;
         order[m++] = (uint8_t)'\n';
+        order[m++] = (uint8_t)'\t';  // rank 96: without it the rarest rank read an uninitialised LDS byte
         uint32_t acc = 0;
         for (int r = 0; r < TEXT_SYMS; r++) {  // Zipf head, geometric tail of rare symbols (long codes)
             const uint32_t w = (r < 64) ? 1000000u / (uint32_t)(r + 1) : (15625u >> ((r - 62) / 2));

@@ -341,6 +341,7 @@ static void text_tables(uint8_t order[ORC_TEXT_SYMS], uint32_t cum[ORC_TEXT_SYMS
     for (int c = '0'; c <= '9'; c++) { order[n++] = (uint8_t)c; used[c] = 1; }
     for (int c = 33; c < 127; c++) if (!used[c]) order[n++] = (uint8_t)c;
     order[n++] = '\n';
+    order[n++] = '\t';  /* rank 96: without it the rarest rank read an uninitialised byte */
     uint32_t acc = 0;
     for (int r = 0; r < ORC_TEXT_SYMS; r++) { /* Zipf head, geometric tail of rare symbols (long codes) */
         uint32_t w = (r < 64) ? 1000000u / (uint32_t)(r + 1) : (15625u >> ((r - 62) / 2));

@@ -84,3 +84,22 @@ def pin_input(orc, pin):
     if "file" in pin:
         return np.fromfile(os.path.join(GOLDEN, pin["file"]), dtype=np.uint8)
     return recipe_bytes(orc, pin["recipe"])
+
+
+TEXT_TOTAL = 4775113  # cum[96] of the text generator's table (oracle/dcz_oracle.c text_tables)
+
+
+def text_rank96_positions(seed, start, n):
+    """Positions i in [0, n) at which the text generator draws its rarest rank (96), by the generator's own arithmetic."""
+    out = []
+    with np.errstate(over="ignore"):
+        for lo in range(0, n, 1 << 22):
+            i = np.arange(lo, min(n, lo + (1 << 22)), dtype=np.uint64)
+            x = np.uint64(seed) + (np.uint64(start) + i) * np.uint64(0x9E3779B97F4A7C15)
+            x = x + np.uint64(0x9E3779B97F4A7C15)
+            x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+            x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+            x = x ^ (x >> np.uint64(31))
+            t = ((x >> np.uint64(32)) * np.uint64(TEXT_TOTAL)) >> np.uint64(32)
+            out.append(lo + np.nonzero(t == np.uint64(TEXT_TOTAL - 1))[0])
+    return np.concatenate(out)

@@ -324,6 +324,23 @@ def test_generators_match_oracle(pkg, svc, orc):
         assert (t.cpu().numpy() == orc.gen_lowentropy(0xD0C5, start, n)).all()
 
 
+def test_text_generator_on_device_defines_its_rarest_symbol(pkg, svc, orc):
+    """dczu_fill_text over a span holding rank-96 draws (the byte that once came from uninitialised LDS) equals the
+    oracle byte for byte, with '\\t' at every such position."""
+    from conftest import text_rank96_positions
+    torch = _torch()
+    n = 24 << 20
+    pos = text_rank96_positions(0xD0C2, 0, n)
+    assert pos.size >= 2
+    t = torch.zeros(n, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    assert pkg.lib().dczu_fill_text(svc.ctx.handle, t.data_ptr(), n, 0xD0C2, 0, None) == 0
+    torch.cuda.synchronize()
+    got = t.cpu().numpy()
+    assert (got[pos] == ord("\t")).all()
+    assert (got == orc.gen_text(0xD0C2, 0, n)).all()
+
+
 def test_capacity_error_is_reported_per_chunk(pkg, svc, orc):
     torch = _torch()
     data = orc.java_random_bytes(9, 4 * 65536)
@@ -1674,3 +1691,41 @@ def test_bench_line_keeps_the_drivers_contract():
     assert cb["kind"] == "port" and cb["cores"] >= 2 and cb["value"] > 0 and "sample" in cb and cb["unit"] == "GB/s"
     for kname, kv in d["kernels"].items():
         assert (kv.get("gbps") or 0.0) <= 8000.0, (kname, kv)
+
+
+def test_bench_dump_outputs_are_the_oracles_and_repeat(orc, tmp_path):
+    """bench.py --dump-outputs, run twice with the same arguments in processes of their own: both runs write the same
+    arrays, and what they hold is what the oracle computes for the same input (payload bytes at the sampled positions,
+    sizes, offsets, code lengths, statuses, total, and the decoded bytes)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n, bb = 64 << 20, 4 << 20
+    runs = []
+    for k in range(2):
+        d = str(tmp_path / ("run%d" % k))
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--workload",
+               "text", "--bytes-per-gpu", str(n), "--no-secondary", "--cpu-sample-mib", "0", "--dump-outputs", d]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["dump_outputs"]["dir"] == d
+        runs.append({nm: np.load(os.path.join(d, nm + ".npy")) for nm in line["dump_outputs"]["arrays"]})
+    a, b = runs
+    assert sorted(a) == sorted(b) == sorted(["payload", "comp_size", "comp_off", "code_lengths", "status", "total", "decoded",
+                                             "decode_status", "decode_errpos"])
+    for nm in a:
+        assert a[nm].dtype == b[nm].dtype and a[nm].shape == b[nm].shape and (a[nm] == b[nm]).all(), nm
+    data = orc.gen_text(0xD0C2, 0, n)
+    pay, sizes, offs, lens = orc.compress_blocks(data, bb)
+    assert a["total"].tolist() == [float(pay.size)]
+    assert (a["comp_size"] == sizes).all() and (a["comp_off"] == offs).all()
+    assert (a["code_lengths"] == lens.reshape(-1)).all()
+    assert (a["status"] == 0).all() and (a["decode_status"] == 0).all()
+    import bench
+    idx = bench._sample_index(np, n, bench.DUMP_CAPS["payload"])
+    assert (a["decoded"] == data[idx]).all()
+    want = np.where(idx < pay.size, pay[np.minimum(idx, pay.size - 1)].astype(np.float32), -1)
+    assert (a["payload"] == want).all()

@@ -155,3 +155,14 @@ def test_synthetic_streams_are_position_keyed(orc):
     assert 0.985 < (z == 0).mean() < 0.995
     lens, _ = orc.build_canonical_codes(orc.histogram(orc.gen_text(0xD0C2, 0, 1 << 20)))
     assert 17 <= lens.max() <= 26  # long enough to leave the reference's 10-bit table
+
+
+def test_text_generator_defines_its_rarest_symbol(orc):
+    """Rank 96 of the text stream is '\\t' (it once read an uninitialised byte, so the stream changed from run to run)."""
+    from conftest import text_rank96_positions
+    n = 24 << 20
+    pos = text_rank96_positions(0xD0C2, 0, n)
+    assert pos.size >= 2
+    data = orc.gen_text(0xD0C2, 0, n)
+    assert (data[pos] == ord("\t")).all()
+    assert int((data == ord("\t")).sum()) == pos.size
